@@ -15,8 +15,16 @@ PoRep partitions are independent proofs -- SURVEY.md 8e), so per-GPU work is fix
 --partitions P runs BASELINE config 5's shape instead: every step proves P partitions round-robin over
 the ranks (10 over 8 GPUs: two rounds on ranks 0 and 1) and all-gathers the P x 192-byte multi-proof.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-rows 26] [--partitions P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-rows 26] [--partitions P] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only the above: setup, W warm-up proofs, the K timed steps, the pairing check of the timed
+proofs, and the result line (`ms_per_step` = the timed region / K).  --dump-outputs DIR writes the last timed
+step's proofs (what the caller of the timed path receives) as DIR/proofs.npy, float32, one value per byte;
+every input is derived from fixed seeds, so two builds can be compared output for output.  --full adds every
+secondary leg after the main one (device-resident witness, one-lane proof, standalone MSM / NTT, params round
+trip, tree C, SDR labels, CPU baseline, uniform witness, config 4, stacked PoRep, Winning / Window PoSt, and
+config 5 on several GPUs); each leg's own switch (--tree-log-nodes 0, --no-cpu-baseline, ...) still applies.
 
 Launch: under torch.distributed.run (WORLD_SIZE set) each process is one rank, and WORLD_SIZE must equal
 --gpus.  Without a launcher, --gpus N > 1 makes this process a parent that, before touching the GPU, starts
@@ -981,7 +989,17 @@ def main():
                     help="1: write the main key as a params file and time its unchecked / checked load (setup_s)")
     ap.add_argument("--tune", action="append", default=[], metavar="NAME=VALUE",
                     help="library A/B switch for the whole run (mi_tune_set, csrc/tune.h; tools' A/B runs only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the main leg, also run every secondary leg (device-resident witness, one-lane proof, "
+                         "standalone MSM / NTT, params round trip, tree C, SDR, CPU baseline, uniform witness, config 4, "
+                         "config 5, stacked PoRep, Winning / Window PoSt); without it only the main leg runs and the "
+                         "legs' own switches are ignored")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (its proofs' bytes) as DIR/proofs.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    full = args.full
     if args.stacked_layers is None or args.stacked_challenges is None:
         from fil_groth16.compound import SECTOR_SIZE_32GIB, porep_layer_challenges
 
@@ -1107,10 +1125,23 @@ def main():
     verified = bool(fg.verify_batch(vk, ic, [pub_inputs] * len(proofs), proofs)) and \
         bool(fg.verify(vk, ic, pub_inputs, proofs[-1]))
     t_ver = time.perf_counter() - t_ver
+    # how the timed proofs planned A's MSM: "own", "shared" (one plan with L) or "derived" (from L's)
+    a_plan = "derived" if ctx.derived_plans() else "shared" if ctx.shared_plans() else "own"
 
+    # --dump-outputs: what a caller of the timed path received in the last timed step, i.e. that step's proofs
+    # (one per rank, or P with --partitions) in gather order, 192 bytes each, one float32 per byte.  Circuit,
+    # witness, toxic waste and blinding factors are all derived from fixed seeds, so the array is the same from
+    # run to run with the same arguments.
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = proofs[-(P if P else world):]
+        np.save(os.path.join(args.dump_outputs, "proofs.npy"),
+                np.frombuffer(b"".join(last), dtype=np.uint8).reshape(len(last), 192).astype(np.float32))
+
+    # Everything below the main leg runs only with --full.
     # secondary: the same proof with the witness already resident in HBM (no upload)
     resident = None
-    if not args.no_device_resident:
+    if full and not args.no_device_resident:
         zdev = torch.from_numpy(sc.z_array().copy()).to(device)
         k2 = max(2, args.steps // 4)
         fg.prove(ctx, pk, circ, zdev.data_ptr(), *blinding(0, 0))
@@ -1128,8 +1159,7 @@ def main():
     # main lane's, on the same stream), so k_accum_level0's launch times are the kernel's own and not stretched by
     # the other lane's sorts and NTTs (the timed proofs' two-lane figure is reported beside it)
     one_lane = None
-    a_plan = None  # how this key's proofs plan A's MSM: "own", "shared" (one plan with L) or "derived" (from L's)
-    if rank == 0:
+    if full and rank == 0:
         try:
             with fg.tuned(prove_lanes=1):
                 ctx.reset_stats()
@@ -1141,85 +1171,86 @@ def main():
             one_lane = {"error": str(e)}
 
     # secondary metric: standalone G1 MSM over the resident 2^log_rows - 1 h-query points
-    msm_n = pk.n_h
-    pts = pk.points(0)
-    rng = np.random.default_rng(7 + rank)
-    sw = rng.integers(0, 2**64, size=(msm_n, 4), dtype=np.uint64)
-    sw[:, 3] &= np.uint64(0x3FFFFFFFFFFFFFFF)
-    sc_dev = torch.from_numpy(sw.view(np.uint8).reshape(-1)).to(device)
-    pts.msm_dev(sc_dev.data_ptr(), msm_n)  # warm
-    ctx.synchronize()
-    tm = time.perf_counter()
-    for _ in range(args.msm_reps):
-        pts.msm_dev(sc_dev.data_ptr(), msm_n)
-    ctx.synchronize()
-    msm_dt = (time.perf_counter() - tm) / args.msm_reps
-    # BASELINE configs[1]: 2^20-point G1 MSM + 2^20-element Fr NTT (device-resident inputs)
-    micro = {}
-    if msm_n >= (1 << 20):
-        m20 = 1 << 20
-        pts.msm_dev(sc_dev.data_ptr(), m20)
+    msm_n, msm_dt, micro = pk.n_h, None, {}
+    if full:
+        pts = pk.points(0)
+        rng = np.random.default_rng(7 + rank)
+        sw = rng.integers(0, 2**64, size=(msm_n, 4), dtype=np.uint64)
+        sw[:, 3] &= np.uint64(0x3FFFFFFFFFFFFFFF)
+        sc_dev = torch.from_numpy(sw.view(np.uint8).reshape(-1)).to(device)
+        pts.msm_dev(sc_dev.data_ptr(), msm_n)  # warm
         ctx.synchronize()
         tm = time.perf_counter()
-        for _ in range(10):
+        for _ in range(args.msm_reps):
+            pts.msm_dev(sc_dev.data_ptr(), msm_n)
+        ctx.synchronize()
+        msm_dt = (time.perf_counter() - tm) / args.msm_reps
+        # BASELINE configs[1]: 2^20-point G1 MSM + 2^20-element Fr NTT (device-resident inputs)
+        if msm_n >= (1 << 20):
+            m20 = 1 << 20
             pts.msm_dev(sc_dev.data_ptr(), m20)
-        ctx.synchronize()
-        t20 = (time.perf_counter() - tm) / 10
-        x = torch.from_numpy(sw[:m20].copy().view(np.uint8).reshape(-1)).to(device)
-        ctx.ntt_dev(x.data_ptr(), 20, False, False)
-        ctx.synchronize()
-        tm = time.perf_counter()
-        for _ in range(10):
+            ctx.synchronize()
+            tm = time.perf_counter()
+            for _ in range(10):
+                pts.msm_dev(sc_dev.data_ptr(), m20)
+            ctx.synchronize()
+            t20 = (time.perf_counter() - tm) / 10
+            x = torch.from_numpy(sw[:m20].copy().view(np.uint8).reshape(-1)).to(device)
             ctx.ntt_dev(x.data_ptr(), 20, False, False)
-        ctx.synchronize()
-        n20 = (time.perf_counter() - tm) / 10
-        # the same 2^20 fixed bases with a window table (mi_points_precompute: T[w n + i] = 2^(c w) P_i, built once
-        # outside the timer, as a key's small queries carry theirs): one bucket set for every window
-        tb = time.perf_counter()
-        pts.precompute(0, m20)
-        ctx.synchronize()
-        tb = time.perf_counter() - tb
-        tinfo = pts.table_info()
-        pts.msm_dev(sc_dev.data_ptr(), m20)
-        ctx.synchronize()
-        tm = time.perf_counter()
-        for _ in range(10):
+            ctx.synchronize()
+            tm = time.perf_counter()
+            for _ in range(10):
+                ctx.ntt_dev(x.data_ptr(), 20, False, False)
+            ctx.synchronize()
+            n20 = (time.perf_counter() - tm) / 10
+            # the same 2^20 fixed bases with a window table (mi_points_precompute: T[w n + i] = 2^(c w) P_i, built once
+            # outside the timer, as a key's small queries carry theirs): one bucket set for every window
+            tb = time.perf_counter()
+            pts.precompute(0, m20)
+            ctx.synchronize()
+            tb = time.perf_counter() - tb
+            tinfo = pts.table_info()
             pts.msm_dev(sc_dev.data_ptr(), m20)
-        ctx.synchronize()
-        t20w = (time.perf_counter() - tm) / 10
-        micro = {"workload": "BASELINE configs[1]: 2^20-point G1 MSM + 2^20-element Fr NTT, device-resident",
-                 "msm_g1_2e20_ms": t20 * 1e3, "msm_g1_2e20_mpoints_per_s": m20 / t20 / 1e6,
-                 "msm_g1_2e20_table_ms": t20w * 1e3, "msm_g1_2e20_table_mpoints_per_s": m20 / t20w / 1e6,
-                 "table": dict(tinfo, build_ms=tb * 1e3, gbytes=tinfo["points"] * tinfo["windows"] * 128 / 1e9,
-                               note="fixed-base window table of the 2^20 bases (built once, outside the timer); "
-                                    "msm_g1_2e20_* is the same MSM without it"),
-                 "ntt_fr_2e20_ms": n20 * 1e3, "ntt_fr_2e20_melems_per_s": m20 / n20 / 1e6}
-        del x
-    del sc_dev, pts
+            ctx.synchronize()
+            tm = time.perf_counter()
+            for _ in range(10):
+                pts.msm_dev(sc_dev.data_ptr(), m20)
+            ctx.synchronize()
+            t20w = (time.perf_counter() - tm) / 10
+            micro = {"workload": "BASELINE configs[1]: 2^20-point G1 MSM + 2^20-element Fr NTT, device-resident",
+                     "msm_g1_2e20_ms": t20 * 1e3, "msm_g1_2e20_mpoints_per_s": m20 / t20 / 1e6,
+                     "msm_g1_2e20_table_ms": t20w * 1e3, "msm_g1_2e20_table_mpoints_per_s": m20 / t20w / 1e6,
+                     "table": dict(tinfo, build_ms=tb * 1e3, gbytes=tinfo["points"] * tinfo["windows"] * 128 / 1e9,
+                                   note="fixed-base window table of the 2^20 bases (built once, outside the timer); "
+                                        "msm_g1_2e20_* is the same MSM without it"),
+                     "ntt_fr_2e20_ms": n20 * 1e3, "ntt_fr_2e20_melems_per_s": m20 / n20 / 1e6}
+            del x
+        del sc_dev, pts
 
     # the key load every prover process does once per shape (get_groth_params -> read_cached_params ->
     # build_mapped_parameters, core/parameter_cache.hpp:124-128,185-200; mmap at mapped_scheme_params.hpp:50-60): the
     # main key written as a v28 params file, loaded back unchecked and subgroup-checked (mi_params_load), and the
     # loaded key's proof compared with the resident key's, outside every timer
     params_load = None
-    if rank == 0 and world == 1 and args.params_roundtrip and not args.params:
+    if full and rank == 0 and world == 1 and args.params_roundtrip and not args.params:
         try:
             params_load = params_roundtrip(fg, ctx, circ, pk, zhost, blinding(0, 0))
         except Exception as e:  # reported, never fatal
             params_load = {"error": str(e)}
         log(rank, f"params round trip: {params_load}")
 
+    if full:
+        log(rank, "secondary: MSM / configs[1] micro done")
     # tree C over one 2^tree_log_nodes-node sub-tree (device-resident labels), and the
     # oracle's CPU Poseidon on a sample of the same columns
-    log(rank, "secondary: MSM / configs[1] micro done")
     tree = None
-    if args.tree_log_nodes and rank == 0:
+    if full and args.tree_log_nodes and rank == 0:
         tree = tree_c_leg(args, fg, ctx, device, world)
         log(rank, "tree C leg done")
 
     # SDR labelling-witness labels (SHA-256 over gathered parents)
     sdr = None
-    if args.sdr_log_labels and rank == 0:
+    if full and args.sdr_log_labels and rank == 0:
         try:
             sdr = sdr_leg(args, fg, ctx, device, world)
         except Exception as e:  # reported, never fatal to the main measurement
@@ -1227,14 +1258,14 @@ def main():
         log(rank, "SDR label leg done")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args, fg, synth_mod, ctx)
         except Exception as e:  # reported, never fatal to the GPU measurement
             cpu = {"value": None, "unit": "constraints/s", "cores": None, "kind": "port", "sample": f"failed: {e}"}
 
     config5 = None
-    if world > 1 and not P and args.post_sectors:
+    if full and world > 1 and not P and args.post_sectors:
         import gc
 
         del pk, circ, zhost, sc
@@ -1246,7 +1277,7 @@ def main():
         except Exception as e:  # reported, never fatal to the main measurement
             config5 = {"error": str(e)}
 
-    if rank == 0 and world == 1 and (args.config4_log_rows or args.stacked_log_nodes or args.post_sectors or
+    if full and rank == 0 and world == 1 and (args.config4_log_rows or args.stacked_log_nodes or args.post_sectors or
                                      args.winning_log_nodes or args.uniform_steps):
         import gc
 
@@ -1254,7 +1285,7 @@ def main():
         gc.collect()
         ctx.synchronize()
     uniform = None
-    if rank == 0 and world == 1 and args.uniform_steps:
+    if full and rank == 0 and world == 1 and args.uniform_steps:
         try:
             log(rank, "uniform-witness leg ...")
             uniform = uniform_leg(args, fg, synth_mod, ctx)
@@ -1262,7 +1293,7 @@ def main():
             uniform = {"value": None, "error": str(e)}
 
     config4 = None
-    if rank == 0 and world == 1 and args.config4_log_rows:
+    if full and rank == 0 and world == 1 and args.config4_log_rows:
         try:
             log(rank, "config 4 leg ...")
             config4 = config4_leg(args, fg, synth_mod, ctx)
@@ -1270,7 +1301,7 @@ def main():
             config4 = {"value": None, "error": str(e)}
 
     stacked_res = None
-    if rank == 0 and world == 1 and args.stacked_log_nodes:
+    if full and rank == 0 and world == 1 and args.stacked_log_nodes:
         try:
             log(rank, "stacked PoRep leg ...")
             stacked_res = stacked_leg(args, fg, ctx, device, world)
@@ -1278,7 +1309,7 @@ def main():
             stacked_res = {"error": str(e)}
 
     winning = None
-    if rank == 0 and world == 1 and args.winning_log_nodes:
+    if full and rank == 0 and world == 1 and args.winning_log_nodes:
         try:
             log(rank, "Winning-PoSt leg ...")
             winning = winning_post_leg(args, fg, ctx, device)
@@ -1286,7 +1317,7 @@ def main():
             winning = {"error": str(e)}
 
     post_res = None
-    if rank == 0 and world == 1 and args.post_sectors and args.post_reps:
+    if full and rank == 0 and world == 1 and args.post_sectors and args.post_reps:
         try:
             log(rank, "Window-PoSt leg ...")
             post_res = window_post_leg(args, fg, ctx, device, rank, world, None, None)
@@ -1380,6 +1411,7 @@ def main():
         "value": value,
         "unit": "constraints/s",
         "n_gpus": world,
+        "full": full,
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3,
@@ -1401,7 +1433,7 @@ def main():
         "h2d": {"ms_per_proof": h2d["ms"] / max(h2d["launches"], 1),
                 "gb_per_s": h2d["units"] / max(h2d["ms"], 1e-9) / 1e6, "bytes_per_proof": 32 * shape["num_vars"]},
         "device_resident": resident,
-        "msm_g1_mpoints_per_s": msm_n / msm_dt / 1e6,
+        "msm_g1_mpoints_per_s": msm_n / msm_dt / 1e6 if msm_dt else None,
         "msm_g1_points": msm_n,
         "config2_micro": micro,
         "roofline": {

@@ -1,6 +1,6 @@
 """GPU: the multi-GPU entry points as the driver runs them, on this pool's one-GPU boxes.
 
-* `bench.py --gpus 2` with no launcher: the parent starts two rank processes itself (bench.spawn_ranks), before
+* `bench.py --full --gpus 2` with no launcher: the parent starts two rank processes itself (bench.spawn_ranks), before
   any GPU call, and forwards rank 0's JSON line.  Both ranks share device 0 and gloo carries the collectives
   (MI_BENCH_SHARED_DEVICE / MI_BENCH_BACKEND: RCCL refuses two ranks on one device); the line must report
   n_gpus 2 and a config-5 leg (3 Window-PoSt partitions of 8 sectors: 0 and 1 whole, 2 split over both ranks)
@@ -32,7 +32,7 @@ def _free_port():
 def test_bench_gpus2_spawns_ranks_and_measures_config5():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MI_BENCH_BACKEND="gloo", MI_BENCH_SHARED_DEVICE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--log-rows", "12", "--msm-reps", "1", "--no-cpu-baseline", "--no-device-resident", "--tree-log-nodes", "0",
            "--sdr-log-labels", "0", "--config4-log-rows", "0", "--stacked-log-nodes", "0", "--winning-log-nodes", "0",
            "--post-sectors", "8", "--post-log-nodes", "12", "--post-partitions", "3"]

@@ -13,7 +13,7 @@ C5=${2:-64}
 C5P=${3:-3}
 mkdir -p gpurun_out/dist
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --log-rows "$LR" --no-cpu-baseline \
+    --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 1 --log-rows "$LR" --no-cpu-baseline \
     --tree-log-nodes 0 --sdr-log-labels 0 --post-sectors "$C5" --post-partitions "$C5P" > gpurun_out/dist/weak.json 2> gpurun_out/dist/weak.err && echo "weak ok: $(cat gpurun_out/dist/weak.json)" &&
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
     --master-port 29518 bench.py --gpus 2 --steps 2 --warmup 1 --log-rows "$LR" --partitions 5 --no-cpu-baseline \

@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export MI_BENCH_BACKEND=gloo MI_BENCH_SHARED_DEVICE=1
 mkdir -p gpurun_out/spawn
 for n in ${RANKS:-4 8}; do
-    timeout -k 10 400 python3 bench.py --gpus $n --steps 2 --warmup 1 --log-rows 16 --msm-reps 1 --no-cpu-baseline \
+    timeout -k 10 400 python3 bench.py --full --gpus $n --steps 2 --warmup 1 --log-rows 16 --msm-reps 1 --no-cpu-baseline \
         --no-device-resident --tree-log-nodes 0 --sdr-log-labels 0 --post-sectors 16 --post-log-nodes 12 \
         --post-partitions 10 > gpurun_out/spawn/n$n.json 2> gpurun_out/spawn/n$n.err || { echo "n=$n failed"; tail -20 gpurun_out/spawn/n$n.err; exit 1; }
     python3 - <<PY

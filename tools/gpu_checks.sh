@@ -7,7 +7,7 @@
 #   suite     the whole GPU suite and smoke(), as the driver runs them
 #   post64    the 64 GiB Window-PoSt partition test with its record lines
 #   witness   the stacked / PoSt witness and Poseidon parity tests
-#   bench     the default bench line (python3 bench.py) into $O/bench.json
+#   bench     the default bench line (python3 bench.py --full) into $O/bench.json
 #   c3ab      the config-3 main leg, default and with each switch of C3AB="name=value ..." (alternated twice)
 #   wpab      the Window-PoSt leg, default and with each switch of WPAB="name=value ..." (--tune A/B)
 # usage: /usr/local/graft/bin/gpurun --timeout 1200 -- bash tools/gpu_checks.sh parity winning
@@ -15,7 +15,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/checks
 mkdir -p $O
-W="python3 bench.py --steps 1 --warmup 0 --log-rows 12 --msm-reps 1 --no-cpu-baseline --no-device-resident --tree-log-nodes 0 --sdr-log-labels 0 --config4-log-rows 0 --stacked-log-nodes 0 --post-sectors 0 --uniform-steps 0"
+W="python3 bench.py --full --steps 1 --warmup 0 --log-rows 12 --msm-reps 1 --no-cpu-baseline --no-device-resident --tree-log-nodes 0 --sdr-log-labels 0 --config4-log-rows 0 --stacked-log-nodes 0 --post-sectors 0 --uniform-steps 0"
 for mode in "$@"; do
   case $mode in
     parity)
@@ -46,7 +46,7 @@ for mode in "$@"; do
           tests/test_gpu_post.py tests/test_gpu_poseidon.py -k "not 64gib" > $O/witness.log 2>&1 || { tail -20 $O/witness.log; exit 1; }
       tail -1 $O/witness.log ;;
     bench)
-      timeout -k 10 900 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+      timeout -k 10 900 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
       tail -c 400 $O/bench.json ;;
     wpab)  # the 32 GiB Window-PoSt leg (two lanes, as the driver bench runs it), default and with each WPAB switch
       for v in default ${WPAB:-}; do
@@ -58,7 +58,7 @@ for mode in "$@"; do
       for rep in 1 2; do
         for v in default ${C3AB:-}; do
           T=(); [ "$v" = default ] || for kv in ${v//,/ }; do T+=(--tune "$kv"); done
-          timeout -k 10 300 python3 bench.py --steps 5 --warmup 1 --msm-reps 1 --no-cpu-baseline --no-device-resident --tree-log-nodes 0 --sdr-log-labels 0 --config4-log-rows 0 --stacked-log-nodes 0 --post-sectors 0 --uniform-steps 0 --winning-log-nodes 0 "${T[@]}" > $O/c3_$v.json 2> $O/c3_$v.err || { tail -5 $O/c3_$v.err; exit 1; }
+          timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 1 --msm-reps 1 --no-cpu-baseline --no-device-resident --tree-log-nodes 0 --sdr-log-labels 0 --config4-log-rows 0 --stacked-log-nodes 0 --post-sectors 0 --uniform-steps 0 --winning-log-nodes 0 "${T[@]}" > $O/c3_$v.json 2> $O/c3_$v.err || { tail -5 $O/c3_$v.err; exit 1; }
           python3 -c "import json; d = json.load(open('$O/c3_$v.json')); print('config3 $v', round(d['ms_per_step'], 2), round(d['value'] / 1e6, 2), 'Mc/s')"
         done
       done ;;

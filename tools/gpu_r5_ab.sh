@@ -13,7 +13,7 @@ for v in ${TEST_VARIANTS:-}; do
 done
 for rep in $(seq 1 "$REPS"); do
   for v in $V; do
-    FILGPU_LIB=crypto3-fil-proofs_amd/build/var/lib_$v.so timeout -k 10 400 python -u bench.py --no-cpu-baseline \
+    FILGPU_LIB=crypto3-fil-proofs_amd/build/var/lib_$v.so timeout -k 10 400 python -u bench.py --full --no-cpu-baseline \
         --no-device-resident --steps ${STEPS:-6} --warmup 1 --msm-reps 2 --tree-log-nodes 0 --sdr-log-labels 0 \
         --config4-log-rows 0 --stacked-log-nodes 0 --uniform-steps 3 --post-reps ${POST_REPS:-1} --winning-reps 10 \
         ${BENCH_ARGS:-} > gpurun_out/ab5/b_${v}_$rep.json 2> gpurun_out/ab5/b_${v}_$rep.err || {

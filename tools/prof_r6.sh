@@ -18,12 +18,12 @@ QUIET=(--no-cpu-baseline --no-device-resident --tree-log-nodes 0 --sdr-log-label
 for mode in "${modes[@]}"; do
   case $mode in
     winpost)
-      B=(python3 bench.py --steps 1 --warmup 0 --log-rows 12 --msm-reps 1 --post-reps 2 --post-share-groups "" "${QUIET[@]}" "${extra[@]}")
+      B=(python3 bench.py --full --steps 1 --warmup 0 --log-rows 12 --msm-reps 1 --post-reps 2 --post-share-groups "" "${QUIET[@]}" "${extra[@]}")
       timeout -k 10 400 rocprofv3 --kernel-trace -d /tmp/wp -o run -- "${B[@]}" > $O/winpost_bench.json 2> $O/winpost_bench.err || { tail -5 $O/winpost_bench.err; exit 1; }
       python3 tools/winning_timeline.py /tmp/wp/run_results.db --reps 1 --md --top 25 > $O/winpost_timeline.md || exit 1
       cat $O/winpost_timeline.md ;;
     c3)
-      B=(python3 bench.py --steps 3 --warmup 1 --msm-reps 1 --post-sectors 0 "${QUIET[@]}" "${extra[@]}")
+      B=(python3 bench.py --full --steps 3 --warmup 1 --msm-reps 1 --post-sectors 0 "${QUIET[@]}" "${extra[@]}")
       timeout -k 10 400 rocprofv3 --kernel-trace -d /tmp/c3 -o run -- "${B[@]}" > $O/c3_bench.json 2> $O/c3_bench.err || { tail -5 $O/c3_bench.err; exit 1; }
       python3 tools/lane_timeline.py /tmp/c3/run_results.db > $O/c3_timeline.txt || exit 1
       python3 - /tmp/c3/run_results.db > $O/c3_top.md <<'PY' || exit 1

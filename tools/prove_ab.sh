@@ -14,7 +14,7 @@ for v in ${TEST_VARIANTS:-}; do
 done
 for rep in $(seq 1 "$REPS"); do
   for v in $V; do
-    FILGPU_LIB=crypto3-fil-proofs_amd/build/var/lib_$v.so timeout -k 10 300 python -u bench.py --no-cpu-baseline \
+    FILGPU_LIB=crypto3-fil-proofs_amd/build/var/lib_$v.so timeout -k 10 300 python -u bench.py --full --no-cpu-baseline \
         --no-device-resident --steps ${STEPS:-5} --warmup 1 --msm-reps 2 ${BENCH_ARGS:-} \
         > gpurun_out/ab/b_${v}_$rep.json 2> gpurun_out/ab/b_${v}_$rep.err || { echo "$v bench FAILED"; exit 1; }
     echo "$v#$rep: $(python3 -c "

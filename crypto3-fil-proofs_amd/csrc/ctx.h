@@ -290,6 +290,12 @@ void ntt_coset_roundtrip(Ctx &c, fr_t *d, unsigned log_n, const fr_t &scale);
 // transform with scale and the canonical epilogue: a <- H (bit-reversed, canonical), cc clobbered.
 // Returns false (nothing launched) when the domain takes a single pass (log_n <= 10).
 bool ntt_coset_qap(Ctx &c, fr_t *a, const fr_t *b, fr_t *cc, unsigned log_n, const fr_t &scale, const fr_t &zinv);
+// The same tail in its linear form, H = zinv (icoset(a b) - iNTT(cc)): cc takes its inverse DIF passes only, the
+// first pass of H's transform multiplies a by b as it loads and the last one subtracts cc and scales by
+// zinv * dinv into canonical form.  a <- H (bit-reversed, canonical), cc clobbered.  fused = false, or a
+// single-pass domain (log_n <= 10), runs the product and the epilogue as kernels of their own.
+void ntt_qap_linear(Ctx &c, fr_t *a, const fr_t *b, fr_t *cc, unsigned log_n, const fr_t &dinv, const fr_t &zinv,
+                    bool fused);
 void ntt_dif_coset_epilogue(Ctx &c, fr_t *d, unsigned log_n, bool inverse, bool inverse_gen, const fr_t &scale,
                             bool to_canonical);
 // d[pos] *= g^(±bitrev(pos)) * scale (scale may be null)

@@ -190,7 +190,10 @@ __device__ __forceinline__ void ntt_rounds(LdsTile &sh, unsigned b, unsigned Tlo
 // Epilogue (last DIF pass only): epi = 1 multiplies the element at global position pos by
 // G^bitrev_L(pos) * scale (coset shift of the bit-reversed coefficients, fused 1/d); epi = 2 also
 // converts to canonical form (icoset: H for the MSM).
-template <bool DIF, bool FUSED = false>
+// QAP (the linear form of H, ntt_qap_linear): bit 0 multiplies each loaded element by aux at the same position
+// (a b on the coset, first pass of H's inverse coset transform); bit 1 is H's epilogue on the last pass,
+// out = (x g^-bitrev(pos) - aux[pos]) scale in canonical form, aux = c's unscaled inverse DIF.
+template <bool DIF, bool FUSED = false, int QAP = 0>
 __global__ void __launch_bounds__(NTT_THREADS) MI_NTT_OCC k_ntt_pass(fr_t *__restrict__ d, unsigned L, unsigned M, unsigned b,
                                                           unsigned Tlog, unsigned Glog, int twiddle,
                                                           const fr29_t *__restrict__ lo,
@@ -198,7 +201,8 @@ __global__ void __launch_bounds__(NTT_THREADS) MI_NTT_OCC k_ntt_pass(fr_t *__res
                                                           const fr29_t *__restrict__ tw10, int epi,
                                                           const fr29_t *__restrict__ glo,
                                                           const fr29_t *__restrict__ ghi, fr_t scale,
-                                                          const fr29_t *__restrict__ tw10b = nullptr) {
+                                                          const fr29_t *__restrict__ tw10b = nullptr,
+                                                          const fr_t *__restrict__ aux = nullptr) {
     __shared__ LdsTile sh;
     const fr29_t *twA = tw10, *twB = tw10b;
     const unsigned tsh = TILE_LOG - b;
@@ -223,6 +227,7 @@ __global__ void __launch_bounds__(NTT_THREADS) MI_NTT_OCC k_ntt_pass(fr_t *__res
         unsigned t = e & (T - 1), i1 = (e >> Tlog) & bmask, g = e >> (Tlog + b);
         uint64_t gi = ((sub0 + g) << M) + ((uint64_t)i1 << Slog) + i20 + t;
         fr29_t x = f29(d[gi]);
+        if (QAP & 1) x = fr29_mul(x, f29(aux[gi]));  // canonical operands (< r): product < 2r
         if (!DIF && twiddle) {
             uint32_t k1 = brev(i1, b);
             uint32_t ex = (uint32_t)(((uint64_t)(i20 + t) * k1) << (32 - M));
@@ -253,6 +258,15 @@ __global__ void __launch_bounds__(NTT_THREADS) MI_NTT_OCC k_ntt_pass(fr_t *__res
             uint32_t k1 = brev(i1, b);
             uint32_t ex = (uint32_t)(((uint64_t)(i20 + t) * k1) << (32 - M));
             if (ex) x = fr29_mul(x, tw29(lo, hi, ex));
+        }
+        if (QAP & 2) {
+            uint32_t ex = brev((uint32_t)gi, L);
+            if (ex) x = fr29_mul(x, tw29(glo, ghi, ex));  // < 2r with or without the product
+            // aux is canonical (< r): x - aux + r lies in (0, 3r).  scale is the canonical integer of
+            // zinv / d, not its Montgomery image, so the product is the canonical H coefficient plus at
+            // most one r: REDC(v s) < 3r r / R + r < 2r, and to_fr takes the r off.
+            d[gi] = to_fr(fr29_mul(fr29_sub_lazy(x, f29(aux[gi]), FrDesc::MOD29), sc29));
+            continue;
         }
         if (DIF && !FUSED && epi) {
             uint32_t ex = brev((uint32_t)gi, L);
@@ -387,6 +401,21 @@ __global__ void k_coset_scale(fr_t *__restrict__ d, unsigned L, uint64_t n, int 
 __global__ void k_scale(fr_t *__restrict__ d, uint64_t n, fr_t s) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) d[i] = d[i] * s;
+}
+// the unfused pieces of the linear QAP chain (single-pass domains, tune qap_fused = 0)
+__global__ void k_mul_into(fr_t *__restrict__ a, const fr_t *__restrict__ b, uint64_t n) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) a[i] = a[i] * b[i];
+}
+// a[pos] = (a[pos] g^-bitrev(pos) - c[pos]) s, canonical
+__global__ void k_qap_linear_epilogue(fr_t *__restrict__ a, const fr_t *__restrict__ c, unsigned L, uint64_t n,
+                                      const fr_t *__restrict__ lo, const fr_t *__restrict__ hi, fr_t s) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t e = brev((uint32_t)i, L);
+    fr_t x = a[i];
+    if (e) x = x * tw_full(lo, hi, e);
+    a[i] = from_mont((x - c[i]) * s);
 }
 __global__ void k_to_mont(fr_t *__restrict__ d, uint64_t n) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -577,6 +606,49 @@ bool ntt_coset_qap(Ctx &c, fr_t *a, const fr_t *b, fr_t *cc, unsigned L, const f
     // the rest of H's inverse coset transform: passes 1.. with the icoset epilogue (canonical output)
     ntt_run(c, a, L, true, true, 2, true, scale, 1);
     return true;
+}
+
+// H in its linear form.  The inverse coset transform is linear and undoes c's coset transform exactly:
+//   H = icoset((a b - c) zinv) = zinv (icoset(a b) - iNTT(c)),
+// for every witness, satisfying or not.  So c takes its inverse DIF passes only (no coset factor, no DIT passes,
+// no 1/d: c_raw = d iNTT(c), bit-reversed), the first pass of H's transform forms a b as it loads, and the last
+// one ends with out[pos] = (x g^-bitrev(pos) - c_raw[pos]) (zinv / d).  The canonical conversion is folded into
+// that factor: it is handed to the kernel as a canonical integer, and a Montgomery product with it is canonical.
+void ntt_qap_linear(Ctx &c, fr_t *a, const fr_t *b, fr_t *cc, unsigned L, const fr_t &dinv, const fr_t &zinv,
+                    bool fused) {
+    if (L > 32) throw std::runtime_error("ntt: domain larger than 2^32");
+    const uint64_t n = 1ull << L;
+    const fr_t s = zinv * dinv;
+    ntt_run(c, cc, L, true, true);
+    auto plan = plan_passes(L);
+    if (!fused || plan.size() < 2) {
+        k_mul_into<<<grid1(n), 256, 0, c.stream>>>(a, b, n);
+        MI_HIP(hipGetLastError());
+        ntt_run(c, a, L, true, true);
+        k_qap_linear_epilogue<<<grid1(n), 256, 0, c.stream>>>(a, cc, L, n, c.tw.gi_lo, c.tw.gi_hi, s);
+        MI_HIP(hipGetLastError());
+        return;
+    }
+    ScopedTimer tm(c, &c.stats.ntt, n);
+    const fr_t s_canon = from_mont(s);
+    const fr29_t *lo = c.tw.lo29[1], *hi = c.tw.hi29[1], *glo = c.tw.lo29[3], *ghi = c.tw.hi29[3];
+    const size_t last = plan.size() - 1;
+    {
+        auto &p = plan[0];
+        k_ntt_pass<true, false, 1><<<(unsigned)p.blocks, NTT_THREADS, 0, c.stream>>>(
+            a, L, p.M, p.b, p.Tlog, p.Glog, p.twiddle, lo, hi, c.tw.iv_1024, 0, glo, ghi, s_canon, nullptr, b);
+    }
+    for (size_t i = 1; i < last; i++) {
+        auto &p = plan[i];
+        k_ntt_pass<true><<<(unsigned)p.blocks, NTT_THREADS, 0, c.stream>>>(a, L, p.M, p.b, p.Tlog, p.Glog, p.twiddle,
+                                                                             lo, hi, c.tw.iv_1024, 0, glo, ghi, s_canon);
+    }
+    {
+        auto &p = plan[last];
+        k_ntt_pass<true, false, 2><<<(unsigned)p.blocks, NTT_THREADS, 0, c.stream>>>(
+            a, L, p.M, p.b, p.Tlog, p.Glog, p.twiddle, lo, hi, c.tw.iv_1024, 0, glo, ghi, s_canon, nullptr, cc);
+    }
+    MI_HIP(hipGetLastError());
 }
 
 void ntt_dif_coset_epilogue(Ctx &c, fr_t *d, unsigned log_n, bool inverse, bool inverse_gen, const fr_t &scale,

@@ -8,6 +8,7 @@
 //     a_j, b_j, c_j = <A_j,z>, <B_j,z>, <C_j,z> for the n circuit rows, then one row "x_i * 0 = 0"
 //     per public input (a = x_i), zero padded to d = 2^ceil(log2(n + n_in));
 //     a,b,c <- coset_fft(ifft(.)); h_ev = (a*b - c) / (g^d - 1); H = icoset_fft(h_ev)[0..d-2]
+//     (run as six transforms: icoset_fft undoes c's coset_fft, H = (icoset_fft(a*b) - ifft(c)) / (g^d - 1))
 //   multiexps: H (h query), L (aux), A (inputs + aux with A-density), B_G1 / B_G2 (B-density)
 //   A = alpha + sum_A + r delta1; B = beta2 + sum_B2 + s delta2;
 //   C = rs delta1 + s alpha + r beta1 + s sum_A + r sum_B1 + H + L.
@@ -1360,9 +1361,9 @@ namespace {
 // One attempt at a proof's MSM sums.  inject_oom (tests, mi_ctx_inject_oom): after the NTT chain, while the
 // auxiliary lane runs, the main lane asks a scratch buffer for more memory than the device has, so the attempt
 // fails the way a short HBM makes it fail.
-// The witness map and the QAP's NTT chain: A z, B z, C z, three coset round trips and (a b - c) / Z, then the
-// inverse coset transform -> the d canonical H coefficients in bit-reversed order (the key's h_perm order),
-// in the context's prover scratch (slot 20, after the Montgomery witness).
+// The witness map and the QAP's NTT chain: A z, B z, C z, the coset round trips of a and b, c's inverse
+// transform and H = zinv (icoset(a b) - c) -> the d canonical H coefficients in bit-reversed order (the key's
+// h_perm order), in the context's prover scratch (slot 20, after the Montgomery witness).
 fr_t *compute_h(Ctx &c, const Circuit &circ, const fr_t *z_dev) {
     hipStream_t st = c.stream;
     const uint64_t d = circ.d, nv = circ.n_in + circ.n_aux;
@@ -1377,13 +1378,18 @@ fr_t *compute_h(Ctx &c, const Circuit &circ, const fr_t *z_dev) {
     fr_t dinv = inverse(to_mont(dd));
     fr_t g = fr_small_mont(7);
     fr_t zinv = inverse(pow_u64(g, d) - fr_t::one());
-    // ifft, * g^i / d, fft on the coset (natural order) for a and b; c's last pass also forms
-    // (a b - c) / Z and starts the inverse coset transform (ntt_coset_qap); tune::QAP_FUSED = 0 runs
-    // the separate division pass (A/B)
+    // ifft, * g^i / d, fft on the coset (natural order) for a and b.  c never goes to the coset: the inverse
+    // coset transform is linear and undoes c's coset transform, H = zinv (icoset(a b) - ifft(c)), so c takes
+    // one inverse transform and H's transform forms a b on its way in and subtracts c on its way out
+    // (ntt_qap_linear).  tune::QAP_LINEAR = 0 restores c's round trip, whose last pass forms (a b - c) / Z
+    // and starts the inverse coset transform (ntt_coset_qap); tune::QAP_FUSED = 0 runs the product / division
+    // and the epilogue as passes of their own on either chain (A/B)
     const bool qap_fused = tune::get(tune::QAP_FUSED, 1) != 0;
     ntt_coset_roundtrip(c, a, L, dinv);
     ntt_coset_roundtrip(c, b, L, dinv);
-    if (!qap_fused || !ntt_coset_qap(c, a, b, cc, L, dinv, zinv)) {
+    if (tune::get(tune::QAP_LINEAR, 1) != 0) {
+        ntt_qap_linear(c, a, b, cc, L, dinv, zinv, qap_fused);
+    } else if (!qap_fused || !ntt_coset_qap(c, a, b, cc, L, dinv, zinv)) {
         ntt_coset_roundtrip(c, cc, L, dinv);
         k_qap_divide<<<grid1(d), 256, 0, st>>>(a, b, cc, d, zinv);
         ntt_dif_coset_epilogue(c, a, L, true, true, dinv, true);  // icoset, canonical H (bit-reversed)

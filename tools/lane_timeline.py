@@ -23,7 +23,8 @@ CLASSES = [
     ("G2 accumulation (B_G2 + second level)", ("k_accum_level0<Fq2>",)),
     ("bucket reduction (G1 + G2)", ("k_bucket_reduce", "k_seg_fold", "k_sum_groups", "k_tree_level",
                                     "k_bucket_affine", "k_glv_merge")),
-    ("NTT (7 transforms) + QAP division", ("k_ntt_pass", "k_qap_divide", "k_ntt_")),
+    ("NTT chain (6 transforms; 7 with qap_linear=0) + QAP product / division",
+     ("k_ntt_pass", "k_qap_divide", "k_ntt_", "k_qap_linear_epilogue", "k_mul_into")),
     ("digits + sort + bounds", ("k_digits", "radix_sort", "k_bounds", "k_l2_digits", "k_chunk", "k_end_to_cnt",
                                 "k_flag_multi", "k_tree_count", "k_tree_heads", "merge_sort", "scan",
                                 "init_lookback", "partition", "reduce_config", "transform")),

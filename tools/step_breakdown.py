@@ -17,7 +17,7 @@ CLASSES = [
     ("G2 accumulation (B_G2 + second level)", ("k_accum_level0<mi::fq2_t>",)),
     ("bucket reduction (G1 + G2)", ("k_bucket_reduce", "k_seg_fold", "k_sum_groups", "k_tree_level",
                                     "k_bucket_affine")),
-    ("NTT (7 transforms)", ("k_ntt_pass",)),
+    ("NTT chain", ("k_ntt_pass",)),
     ("digits + sort + bounds", ("k_digits", "onesweep", "k_bounds", "k_l2_digits", "radix_sort",
                                 "k_chunk", "k_end_to_cnt", "k_flag_multi", "k_tree_count", "k_tree_heads")),
 ]
